@@ -1,7 +1,7 @@
 """Headline benchmark: Swin-T + 8-layer decoder greedy decode, 128 tokens, batches of 64
 384x384x1 images per GPU (BASELINE.json configs[1]; configs[2] when run with N ranks).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,6 +21,30 @@ holds a row's logits bitwise equal between a 2-row and a 160-row chain).  Each G
 pipelines calls through R engine replicas (``pipeline.ReplicaPool``, one host thread and
 one HIP stream each), so one call's decode overlaps the next call's encoder.  Rank 0
 prints one JSON line; ``value`` = all images all ranks processed / max-over-ranks time.
+
+``--cu-split`` (off by default, for A/B runs) gives each replica its own equal share of
+the device's compute units (``isolate_replicas``); docs/replica_nondeterminism.md has the
+finding it served.
+
+A plain run sets up, warms up, times exactly ``--steps`` batches, writes its outputs when
+``--dump-outputs DIR`` is given and prints the line.  ``--full`` adds the passes that take
+runs of their own: the 16-call latency pass (``p50_image_latency_ms``), the single-replica
+latency / roofline pass, the literal config-2 pass and the CPU baseline (each still
+switched off by its ``--no-...`` option).  When the timed batches are no whole number of
+equal calls, ``call_plan`` splits them into calls that differ by one batch, so ``steps``
+in the line is always the ``--steps`` asked for.
+
+``--dump-outputs DIR`` writes, after the timed region, what the timed path returned to its
+caller: the token ids ``[rows, tokens + 1]`` of each replica's last full call, as float32 in
+``DIR/ids_rank<r>_replica<i>.npy`` (of its last call of the plan's largest size: where the
+calls are unequal, which replica gets the smaller ones is up to the pool, and a smaller
+batch can take other kernels), and the
+encoder memory ``[32, M, 256]`` that call's decode read for 32 images evenly spaced over
+its rows, in
+``DIR/memory_rank<r>_replica<i>.npy`` (a float array to compare within a tolerance: one
+changed token changes every token after it).  Each
+replica decodes its own seeded images on every call, so the files depend only on the
+arguments, never on which replica the pool gave the last call to.
 
 ``--gpus N`` (N > 1) without a launcher (no WORLD_SIZE in the environment) starts
 ``torch.distributed.run --nproc-per-node N`` on this file as a child process, before
@@ -70,6 +94,15 @@ def parse():
     ap.add_argument("--chain-batches", dest="chain", type=int, default=None,
                     help="64-image batches per engine call / decode chain (default: auto_chain, 4 or 5; 1 for "
                          "res18trans, whose encoder attends across its batch, and for beam search)")
+    ap.add_argument("--full", action="store_true", default=False,
+                    help="also run what the headline figure does not need: the 16-call latency pass, the "
+                         "single-replica latency / roofline pass, the literal config-2 pass, the CPU baseline")
+    ap.add_argument("--dump-outputs", dest="dump_outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write each replica's last token ids and a 32-image sample of "
+                         "its encoder memory to DIR/<name>.npy (float32)")
+    ap.add_argument("--cu-split", dest="cu_split", action="store_true", default=False,
+                    help="A/B: each replica on its own share of the compute units instead of all of them "
+                         "(isolate_replicas; docs/replica_nondeterminism.md)")
     ap.add_argument("--no-secondary", dest="secondary", action="store_false", default=True,
                     help="skip the literal config-2 pass (64 images per engine call, 4 replicas)")
     ap.add_argument("--cpu-baseline", dest="cpu_baseline", action="store_true", default=True)
@@ -92,10 +125,13 @@ def parse():
         ap.error("--beam is measured on the Swin path")
     if a.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if a.chain is not None and a.chain > 1 and (a.arch != "swin" or a.beam):
         ap.error("--chain-batches > 1 is for the Swin greedy path (the ResNet18-trans encoder attends across its batch)")
     if a.replicas is None:
         a.replicas = 2 if (a.chain is None or a.chain > 1) and a.arch == "swin" and not a.beam else 4
+    a.chain_auto = a.chain is None
     if a.chain is None:
         a.chain = 1 if (a.arch != "swin" or a.beam) else auto_chain(a.steps, a.replicas)
     return a
@@ -116,15 +152,72 @@ def auto_chain(steps, replicas, g_max=10):
     return 4
 
 
-def warm_replicas(pool, step):
+def call_plan(steps, chain, replicas, auto, g_max=10):
+    """Batches of 64 in each timed engine call, in call order; they sum to ``steps``.  Equal
+    calls of ``chain`` batches where that divides the steps.  Otherwise calls that differ by
+    one batch, the larger first: as few as hold at most ``chain`` batches each, or, when the
+    chain length was left to the benchmark (``auto``), the smallest multiple of the replicas
+    that holds at most ``g_max`` each (13 steps on 2 replicas: 7 + 6)."""
+    if steps % chain == 0:
+        return [chain] * (steps // chain)
+    if auto:
+        calls = min(steps, replicas * -(-steps // (g_max * replicas)))
+    else:
+        calls = -(-steps // chain)
+    q, r = divmod(steps, calls)
+    return [q + 1] * r + [q] * (calls - r)
+
+
+def isolate_replicas(pool, n_cu, sharers=1, slot=0):
+    """Give every engine of the pool its own contiguous range of the device's compute units
+    (``Engine.set_cu_mask``): the device's CUs split evenly over ``sharers`` processes on it
+    (this one the ``slot``-th) times the pool's replicas.  ``--cu-split`` only: the A/B
+    arrangement that located the finding in docs/replica_nondeterminism.md.  Returns the
+    ranges as [first, last + 1] per engine; no split (None) for a single engine alone."""
+    parts = sharers * len(pool.engines)
+    if parts < 2:
+        return None
+    span = n_cu // parts
+    if span < 1:
+        raise SystemExit(f"bench.py: {parts} engines on a device of {n_cu} compute units")
+    out = []
+    for i, e in enumerate(pool.engines):
+        first = (slot * len(pool.engines) + i) * span
+        e.set_cu_mask(range(first, first + span))
+        out.append([first, first + span])
+    return out
+
+
+MEMORY_DUMP_ROWS = 32  # images whose encoder memory --dump-outputs keeps (4.7 MB each replica)
+
+
+def dump_outputs(out_dir, rank, ids_per_replica, rows, memories=()):
+    """``--dump-outputs``: the first ``rows`` rows of the token ids of each replica's last
+    full-size call, [rows, tokens + 1], as float32 (ids < 2^24 are exact) in
+    ``out_dir/ids_rank<rank>_replica<i>.npy``, and beside them ``memories[i]``, the encoder
+    memory [n <= MEMORY_DUMP_ROWS, M, 256] of a fixed sample of that call's images, in
+    ``memory_rank<rank>_replica<i>.npy``."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    for i, ids in enumerate(ids_per_replica):
+        np.save(os.path.join(out_dir, f"ids_rank{rank}_replica{i}.npy"), ids[:rows].cpu().numpy().astype(np.float32))
+    for i, mem in enumerate(memories):
+        if len(mem) > MEMORY_DUMP_ROWS:
+            raise ValueError(f"dump_outputs: {len(mem)} memory rows, at most {MEMORY_DUMP_ROWS} are kept")
+        np.save(os.path.join(out_dir, f"memory_rank{rank}_replica{i}.npy"), np.asarray(mem, dtype=np.float32))
+
+
+def warm_replicas(pool, step, items=(0,)):
     """One untimed call on EVERY replica, each engine driven directly (``pool.imap`` gives an
     item to whichever replica is free, so a short warm-up may never reach one): each
     engine's first decode of this (rows, steps, stop) captures and instantiates its 16 graph
     chunks (engine.hip graph_for), which must not land in the timed region.
+    ``items``: one call per entry on each engine (the call sizes the timed region holds).
     Returns the engines warmed, in order."""
     warmed = []
     for e in pool.engines:
-        step(e, 0)
+        for it in items:
+            step(e, it)
         warmed.append(e)
     return warmed
 
@@ -371,10 +464,12 @@ def main():
         else:
             gather = "rccl (mocr_group_gather_ids)"
     H, W = args.image
-    B, S, R, G = args.batch, args.tokens, args.replicas, args.chain
+    B, S, R = args.batch, args.tokens, args.replicas
+    plan = call_plan(args.steps, args.chain, R, args.chain_auto)  # batches per timed engine call
+    G = max(plan)
     BG = B * G  # images per engine call (one encode, one decode chain of BG rows)
     dtype = DTYPE[args.precision]
-    calls = -(-args.steps // G)  # timed engine calls; the line reports calls * G batches
+    calls = len(plan)
     wcalls = -(-args.warmup // G)
 
     # 256 beam-search tokens need a positional table of >= 257 rows (the reference's has 150,
@@ -394,15 +489,29 @@ def main():
             raise SystemExit(f"RCCL communicator counts {rccl_ranks} ranks, WORLD_SIZE is {world}")
     weights = pkg.synth.make_weights(1234, "init", arch=args.arch, max_pos=max_pos)
     pool.load_weights(weights)
+    # ranks that share a device (a box with fewer GPUs than ranks) share its CUs as well
+    n_cu = torch.cuda.get_device_properties(local).multi_processor_count
+    sharers = -(-int(os.environ.get("LOCAL_WORLD_SIZE", "1")) // ndev)
+    slot = int(os.environ.get("LOCAL_RANK", "0")) // ndev
+    cu_split = isolate_replicas(pool, n_cu, sharers, slot) if args.cu_split else None
     # each replica holds its own G batches of this rank's shard, resident in HBM
+    resident = {}  # engine -> its images on the device; a call of fewer batches takes the first rows
     for i, e in enumerate(pool.engines):
         seed0 = 1000 + (rank * R + i) * BG
-        e.set_images(torch.from_numpy(pkg.synth.make_images(BG, H, W, seed0=seed0)).to(dev))
+        resident[id(e)] = torch.from_numpy(pkg.synth.make_images(BG, H, W, seed0=seed0)).to(dev)
+        e.set_images(resident[id(e)])
         if args.arch == "res18trans":
             e.set_encoder_pos(pkg.synth.make_pos_table(5, e.memory_tokens))
+    last_ids = {}  # engine -> the ids its latest full-size call returned (--dump-outputs)
 
-    def step(eng, _k):
+    def step(eng, g):
+        """One engine call over g batches of B (0: all the engine's resident images)."""
         t0 = time.perf_counter()
+        rows = g * B if g else resident[id(eng)].shape[0]
+        if eng.batch != rows:
+            # another call size of a plan with unequal calls: at most once per replica in the
+            # timed region (the larger calls come first), a device-to-device copy
+            eng.set_images(resident[id(eng)][:rows])
         ids = torch.empty((eng.batch, S + 1), dtype=torch.int32, device=dev)
         eng.encode()
         if args.beam:
@@ -410,33 +519,54 @@ def main():
             ids.copy_(torch.from_numpy(r.ids))
         else:
             eng.decode_into(ids, max_steps=S, stop="none")
+        if rows == resident[id(eng)].shape[0]:
+            last_ids[id(eng)] = ids
         return ids, time.perf_counter() - t0
 
     def run(n, pool=pool):
+        """n: a number of full-size calls, or the list of each call's batches."""
         lat = []
-        for ids, dt in pool.imap(step, range(n)):
+        for ids, dt in pool.imap(step, [0] * n if isinstance(n, int) else n):
             # the all-gather of the token streams, in call order: RCCL on device memory, or the
             # host group when ranks share a device; through the pad-and-trim gather any shard
-            # split takes (every rank's call holds BG rows here, so it is one plain gather)
+            # split takes (call k holds the same rows on every rank, so it is one plain gather)
+            rows = ids.shape[0]
             if grp:
-                pkg.parallel.gather_shards(ids, world * BG, world, rank, grp.gather_ids)
+                pkg.parallel.gather_shards(ids, world * rows, world, rank, grp.gather_ids)
             elif world > 1:
-                pkg.parallel.gather_shards(ids.cpu(), world * BG, world, rank,
+                pkg.parallel.gather_shards(ids.cpu(), world * rows, world, rank,
                                            lambda t: pkg.parallel.gather_ids_host(t, world))
             lat.append(dt)
         return lat
 
-    warm_replicas(pool, step)
+    # every call size of the plan on every replica, the largest last (the pooled warm-up and
+    # the first timed calls are of that size)
+    sizes = sorted(set(plan))
+    warm_replicas(pool, step, sizes)
     run(wcalls)
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    lat = run(calls)
+    lat = run(plan)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        # of each replica's last full-size call (every replica ran one: the warm-up ends on
+        # that size), so which replica the pool gave the plan's smaller calls to, and the
+        # kernels a smaller batch takes, change nothing here.  The memory is what that
+        # call's decode read; an engine whose last call was smaller encodes its full
+        # images once more for it, outside the timed region
+        pick = [k * BG // MEMORY_DUMP_ROWS for k in range(MEMORY_DUMP_ROWS)] if BG > MEMORY_DUMP_ROWS else list(range(BG))
+        mems = []
+        for e in pool.engines:
+            if e.batch != BG:
+                e.set_images(resident[id(e)])
+                e.encode()
+            mems.append(e.memory()[pick])
+        dump_outputs(args.dump_outputs, rank, [last_ids[id(e)] for e in pool.engines], BG, mems)
     rank_elapsed = [elapsed]
     if world > 1:
         # every rank's time (an 8-GPU run shows any imbalance); the line's time is the max
@@ -447,12 +577,16 @@ def main():
 
     # the latency half of the metric: at least 16 more loaded calls of the same pipelined
     # configuration (the timed region holds as few as 2 with the driver's --steps 20)
-    lat_pass = run(max(16, 2 * R))
+    lat_pass = None
+    if args.full:
+        lat_pass = run(max(16, 2 * R))
 
     iso = None
-    if rank == 0 and args.isolated:
+    if rank == 0 and args.full and args.isolated:
         # one replica alone: unloaded call latency + HIP-event kernel timing for the roofline
         e = pool.engines[0]
+        if cu_split:
+            e.set_cu_mask(None)  # alone on the device: all of its CUs
         e.set_timing(True)
         ts = []
         for _ in range(3):
@@ -496,14 +630,17 @@ def main():
             iso["serving"] = serving_latency(pkg, weights, args.precision, local)
 
     literal = None
-    if rank == 0 and world == 1 and args.secondary and G > 1:
+    if rank == 0 and world == 1 and args.full and args.secondary and G > 1:
         # BASELINE config 2 read literally: 64 images per engine call (one 64-row chain), 4
         # replicas, images resident; a shorter pass beside the headline
         pool.close()
         lit_pool = pkg.pipeline.ReplicaPool(4, **dict(ekw, max_batch=B))
         lit_pool.load_weights(weights)
         for i, e in enumerate(lit_pool.engines):
-            e.set_images(torch.from_numpy(pkg.synth.make_images(B, H, W, seed0=1000 + i * B)).to(dev))
+            resident[id(e)] = torch.from_numpy(pkg.synth.make_images(B, H, W, seed0=1000 + i * B)).to(dev)
+            e.set_images(resident[id(e)])
+        if args.cu_split:
+            isolate_replicas(lit_pool, n_cu)
         lit_calls = 32
         warm_replicas(lit_pool, step)
         run(8, lit_pool)
@@ -527,7 +664,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    steps = calls * G
+    steps = sum(plan)  # = --steps
     value = world * B * steps / elapsed
     out = {
         "metric": METRIC,
@@ -536,8 +673,9 @@ def main():
         "n_gpus": world,
         "rccl_ranks": rccl_ranks,
         "steps": steps,
-        "warmup": (wcalls + R) * G,
+        "warmup": wcalls * G + R * sum(sizes),
         "warmup_requested": args.warmup,  # rounded up to whole engine calls of G batches
+        "call_batches": plan,  # batches of B in each timed engine call, in call order
         "ms_per_step": elapsed / steps * 1e3,
         "higher_is_better": True,
         "scaling": "weak",
@@ -560,7 +698,7 @@ def main():
                    "images_per_call": BG, "images_in_flight": BG * R,
                    "image": [H, W], "max_tokens": S, "vocab": pkg.synth.VOCAB,
                    "decoder_layers": pkg.synth.N_LAYERS, "parallelism": f"image-parallel x{world}", "gather": gather,
-                   "replicas_per_gpu": R, "batches_per_chain": G, "precision": args.precision,
+                   "replicas_per_gpu": R, "cu_split": cu_split, "batches_per_chain": G, "precision": args.precision,
                    "variant": list(variant), "build": pkg.engine.load_library().mocr_build_tag().decode()},
         "e2e_roofline": {"value": value / world, "unit": "images/sec per GPU", "peak": E2E_ROOFLINE_IMG_S,
                          "frac": value / world / E2E_ROOFLINE_IMG_S,
@@ -569,19 +707,24 @@ def main():
         # complete together
         "p50_call_latency_loaded_ms": statistics.median(lat) * 1e3,
         "latency_samples": len(lat),
-        "warmup_calls": {"per_replica_direct": 1, "pooled": wcalls,
-                         "note": "every replica runs one untimed call (graph capture) before the pooled warm-up"},
+        "warmup_calls": {"per_replica_direct": len(sizes), "pooled": wcalls,
+                         "note": "every replica runs one untimed call of each call size (graph capture) before "
+                                 "the pooled warm-up"},
         "rank_elapsed_s": {"min": min(rank_elapsed), "max": max(rank_elapsed), "all": rank_elapsed},
-        "p50_image_latency_ms": statistics.median(lat_pass) * 1e3,
-        "p90_image_latency_ms": sorted(lat_pass)[max(0, -(-9 * len(lat_pass) // 10) - 1)] * 1e3,
-        "image_latency_samples": len(lat_pass),
-        "latency_note": (f"p50_image_latency_ms: the loaded latency of an image's engine call ({G} batch(es) of "
-                         f"{B} through encode + decode, {R} replicas pipelining), median of "
-                         f"{len(lat_pass)} calls run right after the timed region in the same configuration "
-                         f"(p50_call_latency_loaded_ms is the median of the timed region's {len(lat)}); "
-                         f"p50_image_latency_b1_ms is one 384x384 image alone (B=1); serving_latency_ms is the "
-                         f"reference's serving call (96x320, B=1, im2latex.predict)"),
+        "full": args.full,
     }
+    if lat_pass:
+        out.update({
+            "p50_image_latency_ms": statistics.median(lat_pass) * 1e3,
+            "p90_image_latency_ms": sorted(lat_pass)[max(0, -(-9 * len(lat_pass) // 10) - 1)] * 1e3,
+            "image_latency_samples": len(lat_pass),
+            "latency_note": (f"p50_image_latency_ms: the loaded latency of an image's engine call ({G} batch(es) of "
+                             f"{B} through encode + decode, {R} replicas pipelining), median of "
+                             f"{len(lat_pass)} calls run right after the timed region in the same configuration "
+                             f"(p50_call_latency_loaded_ms is the median of the timed region's {len(lat)}); "
+                             f"p50_image_latency_b1_ms is one 384x384 image alone (B=1); serving_latency_ms is the "
+                             f"reference's serving call (96x320, B=1, im2latex.predict)"),
+        })
     if literal:
         out["config2_literal"] = literal
     if iso:
@@ -593,7 +736,7 @@ def main():
         out["h2d_ms_per_call"] = iso["h2d_ms"]
         out["h2d_note"] = (f"host->device copy of one call's {BG} images ({iso['h2d_bytes'] / 1e6:.0f} MB fp32), "
                            f"outside the timed region; serialised with the calls it would give "
-                           f"{BG * calls / (elapsed + calls * h2d * 1e-3) * world:.0f} img/s (pageable source)")
+                           f"{B * steps / (elapsed + calls * h2d * 1e-3) * world:.0f} img/s (pageable source)")
         rd = roofline_decode(iso["stats"], args.precision, BG, S)
         rg = roofline(iso["stats"], dtype, args.precision, BG)
         ra = roofline(iso["stats"], dtype, args.precision, BG, attention=True)
@@ -618,7 +761,7 @@ def main():
         out["kernel_classes"] = {k: {"launches": v["launches"], "avg_ms": v["total_ms"] / v["launches"],
                                      "tflops": v["flops"] / v["total_ms"] * 1e-9 if v["total_ms"] else None}
                                  for k, v in sorted(iso["stats"].items())}
-    if args.cpu_baseline and world == 1 and args.arch == "swin" and not args.beam:
+    if args.full and args.cpu_baseline and world == 1 and args.arch == "swin" and not args.beam:
         out["cpu_baseline"] = cpu_baseline(args, pkg)
     if not literal:
         pool.close()

@@ -273,7 +273,15 @@ __global__ void __launch_bounds__(256) stem16w_kernel(const float* __restrict__ 
       for (int c = 0; c < 6; ++c) {
         float acc = 0.f;
 #pragma unroll
-        for (int k = 0; k < 16; ++k) acc = fmaf(wr[c][k], px[k], acc);
+        for (int k = 0; k < 16; ++k) {
+          acc = fmaf(wr[c][k], px[k], acc);
+          // acc opaque after every step: hipcc otherwise pairs the chains into v_pk_fma_f32,
+          // and with another engine's fused stage-1 kernels resident on the same CU single
+          // packed FMAs of this kernel came back wrong in lanes 48-63 (one channel of one
+          // token, 200-260 of 640 images, different every run).  Scalar v_fmac_f32 gives the
+          // same bits and repeats (docs/replica_nondeterminism.md)
+          asm volatile("" : "+v"(acc));
+        }
         v[c] = acc + br[c];
         s += v[c];
       }

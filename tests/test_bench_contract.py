@@ -90,6 +90,10 @@ def test_default_run_is_one_gpu_minutes_scale(bench, monkeypatch):
     assert a.gpus == 1 and a.steps == 64 and a.warmup == 4 and a.batch == 64 and a.tokens == 128
     assert a.chain == 8 and a.replicas == 2 and a.precision == "bf16x3" and a.image == [384, 384]
     assert a.cpu_sample == 64 and a.cpu_runs == 3  # B = 64, median of 3
+    assert a.full is False and a.dump_outputs is None  # a plain run: the timed steps and the line only
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == "d" and a.secondary and a.isolated and a.cpu_baseline
     monkeypatch.setattr(sys, "argv", ["bench.py", "--arch", "res18trans"])
     a = bench.parse()
     assert a.chain == 1 and a.replicas == 4  # its encoder attends across its batch of 64
@@ -105,6 +109,121 @@ def test_auto_chain_keeps_timed_calls_even_over_replicas(bench, monkeypatch):
     assert (a.chain, a.replicas) == (10, 2)
     monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "20", "--chain-batches", "4"])
     assert bench.parse().chain == 4
+
+
+def test_call_plan_times_exactly_the_steps_asked_for(bench):
+    """--steps sets the timed batches: equal calls where the chain divides them (the forms
+    above are unchanged), else calls that differ by one batch, the larger first, never
+    more than 10 batches each, and a whole number of calls per replica when there are enough."""
+    assert bench.call_plan(64, 8, 2, True) == [8] * 8 and bench.call_plan(20, 10, 2, True) == [10, 10]
+    assert bench.call_plan(8, 4, 2, True) == [4, 4] and bench.call_plan(6, 1, 4, False) == [1] * 6
+    assert bench.call_plan(13, 4, 2, True) == [7, 6] and bench.call_plan(13, 4, 2, False) == [4, 3, 3, 3]
+    assert bench.call_plan(2, 4, 1, True) == [2] and bench.call_plan(1, 4, 2, True) == [1]
+    assert bench.call_plan(375, 4, 2, True) == [10] * 33 + [9] * 5
+    for replicas in (1, 2, 4):
+        for steps in range(1, 260):
+            plan = bench.call_plan(steps, bench.auto_chain(steps, replicas), replicas, True)
+            assert sum(plan) == steps and max(plan) <= 10 and max(plan) - min(plan) <= 1 and min(plan) >= 1
+            assert plan == sorted(plan, reverse=True)
+            if steps >= 4 * replicas and len(set(plan)) > 1:
+                assert len(plan) % replicas == 0, (steps, replicas, plan)
+
+
+def test_replicas_get_disjoint_compute_units(bench, monkeypatch):
+    """Every engine on the device gets its own CU range: the replicas of one process, and
+    of each process where ranks share a device; a single engine alone keeps all CUs."""
+    class Eng:
+        def __init__(self):
+            self.cus = None
+
+        def set_cu_mask(self, cus):
+            self.cus = list(cus)
+
+    class Pool:
+        def __init__(self, n):
+            self.engines = [Eng() for _ in range(n)]
+
+    p = Pool(2)
+    assert bench.isolate_replicas(p, 256) == [[0, 128], [128, 256]]
+    assert p.engines[0].cus == list(range(128)) and p.engines[1].cus == list(range(128, 256))
+    seen = []
+    for slot in (0, 1):
+        p = Pool(2)
+        assert bench.isolate_replicas(p, 256, sharers=2, slot=slot) == [[128 * slot, 128 * slot + 64],
+                                                                         [128 * slot + 64, 128 * slot + 128]]
+        seen += [c for e in p.engines for c in e.cus]
+    assert sorted(seen) == list(range(256))  # disjoint, and the whole device
+    p = Pool(1)
+    assert bench.isolate_replicas(p, 256) is None and p.engines[0].cus is None
+    # an A/B option: a plain run leaves every replica on all CUs
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    assert bench.parse().cu_split is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--cu-split"])
+    assert bench.parse().cu_split is True
+
+
+def test_dump_outputs_writes_float32_rows(bench, tmp_path):
+    """--dump-outputs: one float32 .npy per replica, the first `rows` rows of its last ids."""
+    import numpy as np
+    import torch
+    ids = [torch.arange(6 * 5, dtype=torch.int32).reshape(6, 5) + 100 * i for i in range(2)]
+    out = tmp_path / "dump" / "nested"
+    bench.dump_outputs(str(out), 3, ids, 4)
+    assert sorted(p.name for p in out.iterdir()) == ["ids_rank3_replica0.npy", "ids_rank3_replica1.npy"]
+    for i in range(2):
+        a = np.load(out / f"ids_rank3_replica{i}.npy")
+        assert a.dtype == np.float32 and a.shape == (4, 5)
+        np.testing.assert_array_equal(a, ids[i][:4].numpy().astype(np.float32))
+
+
+def test_dump_outputs_memory_sample_and_size_cap(bench, tmp_path):
+    """The memory sample beside the ids: float32, at most MEMORY_DUMP_ROWS images per replica,
+    which keeps a dump of the largest configuration (4 replicas, 640-row calls) under 64 MB."""
+    import numpy as np
+    import torch
+    ids = [torch.zeros((640, 129), dtype=torch.int32) for _ in range(4)]
+    mems = [np.full((bench.MEMORY_DUMP_ROWS, 144, 256), i, np.float64) for i in range(4)]
+    bench.dump_outputs(str(tmp_path), 0, ids, 640, mems)
+    files = sorted(tmp_path.iterdir())
+    assert len(files) == 8 and sum(f.stat().st_size for f in files) < 64 * 2 ** 20
+    for i in range(4):
+        m = np.load(tmp_path / f"memory_rank0_replica{i}.npy")
+        assert m.dtype == np.float32 and m.shape == (bench.MEMORY_DUMP_ROWS, 144, 256) and (m == i).all()
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path), 0, ids[:1], 640, [np.zeros((bench.MEMORY_DUMP_ROWS + 1, 144, 256))])
+
+
+def test_compare_dumps_counts_differing_rows(bench, tmp_path):
+    """tools/compare_dumps.py: rows that differ between two --dump-outputs folders, per file."""
+    import numpy as np
+    spec = importlib.util.spec_from_file_location("compare_dumps", os.path.join(REPO, "tools", "compare_dumps.py"))
+    cd = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(cd)
+    a, b = tmp_path / "a", tmp_path / "b"
+    a.mkdir()
+    b.mkdir()
+    x = np.arange(24, dtype=np.float32).reshape(4, 3, 2)
+    y = x.copy()
+    y[2, 1, 0] += 0.5
+    np.save(a / "ids.npy", x)
+    np.save(b / "ids.npy", x)
+    np.save(a / "memory.npy", x)
+    np.save(b / "memory.npy", y)
+    np.save(a / "only_a.npy", x)
+    assert cd.compare(str(a), str(b)) == [("ids.npy", 0, 4, 0.0), ("memory.npy", 1, 4, 0.5), ("only_a.npy", None, 4, None)]
+    assert cd.compare(str(a), str(b), atol=1.0)[1] == ("memory.npy", 0, 4, 0.5)
+
+
+def test_warmup_runs_every_call_size_on_every_replica(bench):
+    """A plan with unequal calls: each replica is warmed with each size, the largest last."""
+    class Pool:
+        engines = ["e0", "e1", "e2"]
+
+    seen = []
+    plan = bench.call_plan(13, 4, 2, True)
+    warmed = bench.warm_replicas(Pool, lambda e, g: seen.append((e, g)), sorted(set(plan)))
+    assert warmed == Pool.engines
+    assert seen == [(e, g) for e in Pool.engines for g in (6, 7)]
 
 
 def test_gpus_without_launcher_starts_torchrun_child(bench, monkeypatch):

@@ -176,28 +176,72 @@ def test_rccl_gather_of_engine_ids(pkg, golden):
     eng.close()
 
 
-def test_bench_two_ranks_torchrun():
+def test_bench_two_ranks_torchrun(tmp_path):
     """bench.py's N > 1 path under torch.distributed.run (2 ranks; on a one-GPU box both
     share cuda:0, so the token streams are gathered over the host group): one JSON line
-    from rank 0 with the whole-job throughput."""
+    from rank 0 with the whole-job throughput, exactly the --steps asked for timed, and
+    every rank's --dump-outputs files."""
     import json
     import subprocess
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), os.path.join(REPO, "bench.py"),
-           "--gpus", "2", "--steps", "2", "--warmup", "1", "--replicas", "1", "--no-isolated", "--no-cpu-baseline"]
+           "--gpus", "2", "--steps", "3", "--warmup", "1", "--replicas", "1", "--no-isolated", "--no-cpu-baseline",
+           "--dump-outputs", str(tmp_path)]
     r = subprocess.run(cmd, cwd=REPO, env=env, capture_output=True, text=True, timeout=280)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
     out = json.loads(lines[0])
     cfg = out["config"]
+    assert out["steps"] == 3 and out["call_batches"] == [3] and out["full"] is False
+    assert "p50_image_latency_ms" not in out and "config2_literal" not in out and "cpu_baseline" not in out
+    for rank in (0, 1):
+        ids = np.load(tmp_path / f"ids_rank{rank}_replica0.npy")
+        mem = np.load(tmp_path / f"memory_rank{rank}_replica0.npy")
+        assert ids.dtype == np.float32 and ids.shape == (3 * 64, cfg["max_tokens"] + 1)
+        assert (ids[:, 0] == 1).all() and (ids >= 0).all() and (ids < cfg["vocab"]).all()  # column 0 = sos
+        assert mem.dtype == np.float32 and mem.shape == (32, 144, 256) and np.isfinite(mem).all()
     assert out["n_gpus"] == 2 and out["value"] > 0 and cfg["global_batch"] == 2 * cfg["per_gpu_batch"]
     assert cfg["per_gpu_batch"] == cfg["batch_unit"] == 64
     assert cfg["images_per_call"] == cfg["batch_unit"] * cfg["batches_per_chain"]
     assert len(out["rank_elapsed_s"]["all"]) == 2 and out["rank_elapsed_s"]["max"] * 1e3 / out["steps"] == \
         pytest.approx(out["ms_per_step"])
     assert out["config"]["gather"] in ("rccl (mocr_group_gather_ids)", "gloo host (ranks share a device)")
+
+
+def test_bench_plain_run_unequal_calls(tmp_path):
+    """A plain one-GPU run whose timed batches are no whole number of equal calls:
+    ``--steps 5 --chain-batches 2`` on 2 replicas plans calls of 2, 2 and 1 batches, so an
+    engine changes its batch inside the timed region (128 rows, then 64: stage 3 takes
+    other kernels from 128 images on).  Exactly 5 steps are timed, the line holds none of
+    the passes behind --full (no ``--no-...`` option is given), and the dump is each
+    replica's full-size call: 128 rows of ids and the 32-image memory sample."""
+    import json
+    import subprocess
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "1",
+           "--chain-batches", "2", "--replicas", "2", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=REPO, capture_output=True, text=True, timeout=280)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["steps"] == 5 and out["call_batches"] == [2, 2, 1] and out["latency_samples"] == 3
+    assert out["value"] == pytest.approx(64 * 5 / (out["ms_per_step"] * 5e-3)) and out["full"] is False
+    assert out["config"]["cu_split"] is None and out["config"]["images_per_call"] == 128
+    assert out["warmup_calls"]["per_replica_direct"] == 2  # both call sizes on both replicas
+    for key in ("p50_image_latency_ms", "p90_image_latency_ms", "config2_literal", "cpu_baseline", "roofline",
+                "p50_call_latency_unloaded_ms", "p50_image_latency_b1_ms", "serving_latency_ms", "kernel_classes"):
+        assert key not in out, key
+    assert sorted(p.name for p in tmp_path.iterdir()) == [f"{kind}_rank0_replica{i}.npy" for kind in ("ids", "memory")
+                                                          for i in (0, 1)]
+    for i in (0, 1):
+        ids = np.load(tmp_path / f"ids_rank0_replica{i}.npy")
+        mem = np.load(tmp_path / f"memory_rank0_replica{i}.npy")
+        assert ids.dtype == np.float32 and ids.shape == (128, 129) and (ids[:, 0] == 1).all()
+        assert mem.dtype == np.float32 and mem.shape == (32, 144, 256) and np.isfinite(mem).all()
+    # the replicas hold different images
+    assert not np.array_equal(np.load(tmp_path / "ids_rank0_replica0.npy"), np.load(tmp_path / "ids_rank0_replica1.npy"))
 
 
 def test_uneven_shards_decode_sharded(pkg, golden):

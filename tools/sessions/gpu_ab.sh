@@ -9,7 +9,7 @@ L=handwritten-math-ocr-api_amd/lib_var
 for rep in 1 2; do
   for v in base "$@"; do
     arg=""; [ "$v" != base ] && arg="--lib $L/$v/libmathocr.so"
-    timeout -k 10 300 python -u bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $arg > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err || { echo "BENCH $v FAILED"; tail $O/bench_${v}_$rep.err; exit 1; }
+    timeout -k 10 300 python -u bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-secondary $arg > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err || { echo "BENCH $v FAILED"; tail $O/bench_${v}_$rep.err; exit 1; }
     python -c "
 import json; d=json.load(open('$O/bench_${v}_$rep.json')); k=d['kernel_classes']
 enc=d['gpu_time_share']['encoder_ms_per_call']; dec=d['gpu_time_share']['decode_ms_per_call']

@@ -9,8 +9,8 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -v -rP --timeout 300 --tim
 tail -1 $O/tests.log
 timeout -k 10 180 python -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1 || { echo "SMOKE FAILED"; tail -20 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-timeout -k 10 500 python -u bench.py > $O/bench_default.json 2> $O/bench_default.err || { echo "BENCH FAILED"; tail $O/bench_default.err; exit 1; }
+timeout -k 10 500 python -u bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { echo "BENCH FAILED"; tail $O/bench_default.err; exit 1; }
 python -c "import json; d=json.load(open('$O/bench_default.json')); print('default', d['value'], d['ms_per_step'], d['roofline']['frac'], d.get('config2_literal',{}).get('value'))"
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || { echo "BENCH DRIVER FAILED"; tail $O/bench_driver.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || { echo "BENCH DRIVER FAILED"; tail $O/bench_driver.err; exit 1; }
 python -c "import json; d=json.load(open('$O/bench_driver.json')); print('driver', d['value'], d['ms_per_step'])"
 echo done

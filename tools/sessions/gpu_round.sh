@@ -19,11 +19,11 @@ if [ "${2:-}" != notests ]; then
     || { echo "SMOKE FAILED"; tail -20 $O/smoke.log; exit 1; }
   tail -2 $O/smoke.log
 fi
-timeout -k 10 600 python -u bench.py > $O/bench.json 2> $O/bench.err \
+timeout -k 10 600 python -u bench.py --full > $O/bench.json 2> $O/bench.err \
   || { echo "BENCH FAILED"; tail -20 $O/bench.err; exit 1; }
 cut -c1-400 $O/bench.json
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_bench -o run -- \
-  python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline > $O/prof_bench.log 2>&1 \
+  python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $O/prof_bench.log 2>&1 \
   || { echo "ROCPROF FAILED"; tail -20 $O/prof_bench.log; exit 1; }
 python3 tools/trace_phase_stats.py $O/prof_bench/run_kernel_trace.csv "mlp384_kernel<3>" 6 \
   --json $O/trace_iso_s3mlp.json > /dev/null || echo "trace phase stats failed"

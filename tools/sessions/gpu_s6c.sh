@@ -9,7 +9,7 @@ timeout -k 10 600 python -u -m pytest tests -m gpu -x -v -rP --timeout 300 --tim
 tail -1 $O/tests.log
 timeout -k 10 180 python -c 'import __graft_entry__ as g; g.smoke()' > $O/smoke.log 2>&1 || { echo "SMOKE FAILED"; tail -20 $O/smoke.log; exit 1; }
 tail -2 $O/smoke.log
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || { echo "BENCH DRIVER FAILED"; tail $O/bench_driver.err; exit 1; }
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 > $O/bench_driver.json 2> $O/bench_driver.err || { echo "BENCH DRIVER FAILED"; tail $O/bench_driver.err; exit 1; }
 python -c "
 import json; d=json.load(open('$O/bench_driver.json')); k=d['kernel_classes']
 print('driver', d['value'], d['ms_per_step'], 'dec', d['roofline']['avg_step_ms'], 'gemm', d['roofline_gemm']['kernel'], d['roofline_gemm']['frac'])

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel duration statistics of the bench's isolated phase, from a rocprofv3
-kernel trace of `bench.py` (run_kernel_trace.csv).
+kernel trace of `bench.py --full` (run_kernel_trace.csv).
 
 bench.py measures the roofline kernels with HIP events while ONE replica runs alone,
 after the loaded (all-replica) timed region.  rocprofv3 --stats averages every dispatch
